@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: this process spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                  (+ what the last timed step returned, as DIR/<name>.npy)
 
 A "step" is one HeteroFusion forward (bevformer_point_pillar_hetero.py:39-49) on one synthetic
 scene of BASELINE.json configs[1]: 5 LiDAR agents, 200x704 BEV, C=256, window 8, 2 iterations,
@@ -41,6 +42,7 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                 reach ego 0's output row; this is the same forward without those two shortcuts.
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -73,6 +75,30 @@ DTYPE = {
 }
 TOLERANCE = {"f16": 1e-3, "split": 1e-4, "mixed": 1e-4, "f32": 1e-4}
 ES = {"f16": 2, "split": 4, "mixed": 2, "f32": 4}      # bytes per stored activation element (Q / K' / V' / O planes)
+DUMP_BYTES = 32 * 2 ** 20                  # --dump-outputs: data bytes of all arrays together (half the 64 MB allowance)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: the arrays the timed path returned in its last step, as DIR/<name>.npy in float32 (float64 stays
+    float64), so that two builds can be compared output for output on the same seeded inputs.  Each array gets an equal share of
+    DUMP_BYTES; one larger than its share is written as a sample: the elements of its flattened form at indices drawn without
+    replacement by numpy.random.default_rng(0), in ascending order - the same indices in every run of the same shape.  The inference
+    forward is bit-reproducible; a --train dump is not (float atomics in the backward pass, amplified by AdamW): compare it to a tolerance.
+    Returns what was written, per array, for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        info = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        keep = DUMP_BYTES // len(arrays) // a.itemsize
+        if a.size > keep:
+            info["sampled_elements"] = keep
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = info
+    return written
 
 
 def phase_work(c, num_iters, es):
@@ -348,25 +374,30 @@ def train_bench(args, c, dev, rank, world, scene, make, barrier, D):
 
     def step(sync_grads=True):
         opt.zero_grad()
-        if world > 1 and not sync_grads:
-            with model.no_sync():
-                (model(*scene) - target).pow(2).mean().backward()
-        else:
-            (model(*scene) - target).pow(2).mean().backward()
+        with model.no_sync() if world > 1 and not sync_grads else contextlib.nullcontext():
+            y = model(*scene)
+            loss = (y - target).pow(2).mean()
+            loss.backward()
         opt.step()
+        return y.detach(), loss.detach()
 
     def timed(n, sync_grads):
         barrier()
         t0 = time.perf_counter()
-        for _ in range(n):
+        for _ in range(n - 1):
             step(sync_grads)
+        last = step(sync_grads)
         barrier()
-        return D.max_over_ranks(time.perf_counter() - t0, dev)
+        return D.max_over_ranks(time.perf_counter() - t0, dev), last
 
     for _ in range(max(1, args.warmup)):
         step()
-    dt = timed(args.steps, True)
-    dt_local = timed(args.steps, False) if world > 1 else dt
+    dt, last = timed(args.steps, True)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"fusion_out": last[0], "loss": last[1]})
+    del last
+    dt_local = timed(args.steps, False)[0] if world > 1 else dt
     n_grad = sum(p.numel() for p in net.parameters() if p.grad is not None)
     ar_ms = None
     if world > 1:
@@ -389,6 +420,8 @@ def train_bench(args, c, dev, rank, world, scene, make, barrier, D):
            "ms_per_step_no_sync": dt_local / args.steps * 1e3,
            "allreduce_exposed_ms": max(0.0, (dt - dt_local) / args.steps * 1e3),
            "allreduce_standalone_ms": ar_ms, "gradient_bytes": 4 * n_grad}
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if not args.stub:
         res["peak_memory_GiB"] = torch.cuda.max_memory_allocated(dev) / 2 ** 30
     return res
@@ -440,7 +473,12 @@ def main(argv=None):
     ap.add_argument("--train", action="store_true",
                     help="the training half of north_star instead of the inference headline: one DistributedDataParallel train step "
                          "per rank (HeteroFusion forward with dropout + HIP backward + gradient all-reduce on RCCL + AdamW)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step returned as DIR/<name>.npy (float32; a larger "
+                         "output as a fixed seeded sample, at most 32 MiB in all): the forward's fused map, with --train also the loss")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_baseline_full:
         print(json.dumps(cpu_baseline_full(CONFIGS[args.config], args.num_iters, 1, args.cpu_threads)), flush=True)
@@ -485,7 +523,7 @@ def main(argv=None):
         D = _u.module_from_spec(spec)
         spec.loader.exec_module(D)
         precision = "stub"
-        a = torch.randn(64, 64)
+        a = torch.randn(64, 64, generator=torch.Generator().manual_seed(0))
 
         def make(_):
             return lambda *s: (a @ a).sum()
@@ -509,12 +547,13 @@ def main(argv=None):
                 net(*scene)
             barrier()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 net(*scene)
+            last = net(*scene)              # what the last step returned (--dump-outputs)
             barrier()
         dt = time.perf_counter() - t0
         # job time = slowest rank; units = what all ranks processed (hm-vit_amd/dist.py)
-        return D.max_over_ranks(dt, dev), D.sum_over_ranks(float(steps), dev)
+        return D.max_over_ranks(dt, dev), D.sum_over_ranks(float(steps), dev), last
 
     if args.train:
         result = train_bench(args, c, dev, rank, world, scene, make, barrier, D)
@@ -526,8 +565,10 @@ def main(argv=None):
         return
 
     net = make(precision)
-    dt, units = timed(net, args.steps, args.warmup)
+    dt, units, last = timed(net, args.steps, args.warmup)
     value = units / dt
+    dumped = dump_outputs(args.dump_outputs, {"fusion_out": last}) if args.dump_outputs and rank == 0 else None
+    del last
 
     result = {
         "metric": "fused BEV scenes/sec (5 agents, 200x704 BEV, C=256)" if args.config == "cfg2"
@@ -553,6 +594,8 @@ def main(argv=None):
         result["config"] = {"workload": "stub (CPU stand-in: launch / barrier / reduction logic only)",
                             "parallelism": f"{world} ranks, backend {args.backend}"}
         result["data"] = "stub"
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     def roofline_of(net, prec):
         """Per-phase HIP-event times of one forward on the launch stream (median of 5), the dominant phase's roofline."""
@@ -732,7 +775,7 @@ def main(argv=None):
             # the opt-in local-stage kernels of round 6: same results, fewer vector-memory wave loads
             for which, key in ((1, "patch_attention"), (2, "patch16_attention")):
                 net.patch_attention = which
-                pdt, _ = timed(net, args.steps, args.warmup)
+                pdt = timed(net, args.steps, args.warmup)[0]
                 _, pph = roofline_of(net, precision)
                 result[key] = {"value": args.steps / pdt, "unit": "scenes/s", "ms_per_step": pdt / args.steps * 1e3, "phases": pph,
                                "note": f"HeteroFusion.patch_attention = {which}: the local stages' attention on "
@@ -742,7 +785,7 @@ def main(argv=None):
         torch.cuda.empty_cache()
         if side and precision != "f16":
             fast = make("f16")
-            fdt, _ = timed(fast, args.steps, args.warmup)
+            fdt = timed(fast, args.steps, args.warmup)[0]
             roof, ph = roofline_of(fast, "f16")
             result["fast_f16"] = {"value": args.steps / fdt, "unit": "scenes/s", "ms_per_step": fdt / args.steps * 1e3,
                                   "dtype": DTYPE["f16"], "tolerance": "1e-3 rel-max (north_star's figure), goldens g12 / g13",
@@ -751,7 +794,7 @@ def main(argv=None):
             torch.cuda.empty_cache()
         if side and precision != "mixed" and c["C"] == 256:
             mixed = make("mixed")
-            mdt, _ = timed(mixed, args.steps, args.warmup)
+            mdt = timed(mixed, args.steps, args.warmup)[0]
             roof, ph = roofline_of(mixed, "mixed")
             result["mixed_a16"] = {"value": args.steps / mdt, "unit": "scenes/s", "ms_per_step": mdt / args.steps * 1e3,
                                    "dtype": DTYPE["mixed"],

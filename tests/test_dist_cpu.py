@@ -107,3 +107,51 @@ def test_bench_train_mode_two_ranks_ddp():
     assert r["value"] > 0 and abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3e-3)) / r["value"] < 1e-6
     assert r["gradient_bytes"] == 4 * (64 * 64 + 64)              # the unused Linear(8, 8) has no gradient
     assert r["allreduce_standalone_ms"] > 0 and r["ms_per_step_no_sync"] > 0 and r["allreduce_exposed_ms"] >= 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: what the last timed step returned lands in DIR as float32 .npy, bit-identical in two runs with the same
+    arguments (seeded inputs); with --train the loss rides along; `--steps` below 1 is refused.  CPU stand-in workload: this
+    exercises bench.py's writing path, not the kernels (tests/test_hip_fusion.py::test_bench_dump_outputs_is_the_timed_forward)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(*extra):
+        return subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--warmup", "1", "--stub", *extra],
+                              env=env, capture_output=True, timeout=300)
+
+    dumps = []
+    for d in ("a", "b"):
+        out = run("--steps", "3", "--dump-outputs", str(tmp_path / d))
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        r = json.loads(out.stdout.decode().strip().splitlines()[-1])
+        assert r["steps"] == 3 and r["dump_outputs"] == {"dir": str(tmp_path / d), "arrays": {"fusion_out": {"shape": [], "dtype": "float32"}}}
+        dumps.append(np.load(tmp_path / d / "fusion_out.npy"))
+    assert dumps[0].dtype == np.float32 and np.array_equal(dumps[0], dumps[1])
+    out = run("--train", "--steps", "2", "--dump-outputs", str(tmp_path / "t"))
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    assert sorted(os.listdir(tmp_path / "t")) == ["fusion_out.npy", "loss.npy"]
+    y, loss = np.load(tmp_path / "t" / "fusion_out.npy"), np.load(tmp_path / "t" / "loss.npy")
+    assert y.shape == (4, 64) and y.dtype == loss.dtype == np.float32 and loss.shape == ()
+    assert abs(float(loss) - float((y.astype(np.float64) ** 2).mean())) < 1e-5 * float(loss)    # the step's loss: mse against zeros
+    out = run("--steps", "0")
+    assert out.returncode != 0 and b"--steps" in out.stderr
+
+
+def test_bench_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """An output larger than its share of the dump budget is written as the elements at the sorted flat indices that
+    numpy.random.default_rng(0) draws without replacement; float64 stays float64, every other dtype becomes float32."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    written = bench.dump_outputs(str(tmp_path), {"big": torch.arange(10000, dtype=torch.int32).reshape(100, 100),
+                                                 "small": torch.ones(3, dtype=torch.float64)})
+    assert written == {"big": {"shape": [100, 100], "dtype": "float32", "sampled_elements": 512},
+                       "small": {"shape": [3], "dtype": "float64"}}
+    big = np.load(tmp_path / "big.npy")
+    assert big.dtype == np.float32 and np.array_equal(big, np.sort(np.random.default_rng(0).choice(10000, 512, replace=False)))
+    assert np.load(tmp_path / "small.npy").dtype == np.float64

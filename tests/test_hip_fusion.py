@@ -474,6 +474,31 @@ def test_full_size_forward_is_bit_reproducible(precision):
             assert torch.equal(net(*scene), y0)
 
 
+def test_bench_dump_outputs_is_the_timed_forward(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what its last timed forward returned: the same bits as a forward of the same seeded
+    module on the same seeded scene in this process (the shipped 128 x 128 size, small enough to be written whole)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    import hmvit_amd
+    from hmvit_amd import synthetic as S
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--config", "native", "--steps", "3", "--warmup", "1",
+                          "--no-strict", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    r = json.loads(out.stdout.decode().strip().splitlines()[-1])
+    assert r["steps"] == 3 and r["dump_outputs"]["arrays"] == {"fusion_out": {"shape": [1, 256, 128, 128], "dtype": "float32"}}
+    c = bench.CONFIGS["native"]
+    cfg = S.make_config(c["C"], c["window"], c["L"], voxel=c["voxel"], downsample=c["downsample"], num_iters=2)
+    net = S.seeded_fusion(cfg, precision=hmvit_amd.REFERENCE_PRECISION, seed=0).cuda().eval()
+    with torch.no_grad():
+        y = net(*_cuda(*S.synthetic_scene(c["L"], c["C"], c["H"], c["W"], c["modes"], seed=1))).cpu().numpy()
+    assert np.array_equal(np.load(tmp_path / "fusion_out.npy"), y)
+
+
 @pytest.mark.parametrize("C,dim_head,window,H,W,arch", [
     (64, 16, 4, 16, 24, "sequential"),      # dim_head 16 on the tuned window
     (128, 64, 8, 16, 32, "sequential"),     # dim_head 64
