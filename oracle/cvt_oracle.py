@@ -92,7 +92,7 @@ def cross_view_attention(x, grid, feature, I_inv, E_inv, sd: Dict[str, Tensor], 
     """CrossViewAttention.forward (cvt_modules.py:216-280).  x (b, dim, H, W); grid (3, H, W) = BEVEmbedding.grid;
     feature (b, n, feat_dim, h, w); I_inv (b, n, 3, 3); E_inv (b, n, 4, 4)."""
     b, n, feat_dim, h, w = feature.shape
-    pixel = generate_grid(h, w)[None].to(x.dtype)
+    pixel = generate_grid(h, w)[None].to(x.device, x.dtype)
     pixel[:, :, 0] *= cfg["image_width"]
     pixel[:, :, 1] *= cfg["image_height"]
     c = E_inv[..., -1:]
@@ -106,7 +106,7 @@ def cross_view_attention(x, grid, feature, I_inv, E_inv, sd: Dict[str, Tensor], 
     d_embed = F.conv2d(d_flat, sd["img_embed.weight"])
     img_embed = d_embed - c_embed
     img_embed = img_embed / (img_embed.norm(dim=1, keepdim=True) + 1e-7)
-    world = grid[:2].to(x.dtype)
+    world = grid[:2].to(x.device, x.dtype)
     w_embed = F.conv2d(world[None], sd["bev_embed.weight"], sd["bev_embed.bias"])
     bev_embed = w_embed - c_embed
     bev_embed = bev_embed / (bev_embed.norm(dim=1, keepdim=True) + 1e-7)

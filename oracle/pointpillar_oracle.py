@@ -5,8 +5,8 @@ Plain-PyTorch fp32 restatement, in eval mode, of ``PointPillar.forward`` with
 -> BaseBEVBackbone -> DownsampleConv.  Takes the reference's ``state_dict`` (same key names).
 Imported only by tests (and by nothing in the shipped package).
 
-Parity status: PINNED by tests/golden/g7_pointpillar.npz (reference imported in the build
-container by tests/golden/make_goldens.py).
+Parity status: PINNED by tests/golden/g7_pointpillar.npz and, at the shipped 512 x 512 / [3, 5, 8]
+size, g19_pointpillar_full.npz (reference imported in the build container by tests/golden/make_goldens.py).
 """
 from __future__ import annotations
 
@@ -33,7 +33,7 @@ def pillar_vfe(voxel_features: Tensor, voxel_num_points: Tensor, coords: Tensor,
     f_center = xyz - centre[:, None, :]
     feats = torch.cat([voxel_features, f_cluster, f_center], dim=-1)             # (Nv, 32, 10)
     n_pts = feats.shape[1]
-    valid = voxel_num_points.view(-1, 1).int() > torch.arange(n_pts, dtype=torch.int).view(1, -1)
+    valid = voxel_num_points.view(-1, 1).int() > torch.arange(n_pts, dtype=torch.int, device=voxel_num_points.device).view(1, -1)
     feats = feats * valid.unsqueeze(-1).to(feats.dtype)                           # padded points zeroed AFTER augmentation
     p = f"{prefix}.pfn_layers.0"
     x = F.linear(feats, sd[f"{p}.linear.weight"])
@@ -45,7 +45,7 @@ def pillar_vfe(voxel_features: Tensor, voxel_num_points: Tensor, coords: Tensor,
 def scatter(pillar_features: Tensor, coords: Tensor, n_agents: int, ny: int, nx: int) -> Tensor:
     """PointPillarScatter.forward (sub_modules/point_pillar_scatter.py:14-47): index z + y*nx + x."""
     C = pillar_features.shape[1]
-    out = torch.zeros(n_agents, C, ny * nx, dtype=pillar_features.dtype)
+    out = torch.zeros(n_agents, C, ny * nx, dtype=pillar_features.dtype, device=pillar_features.device)
     for b in range(n_agents):
         m = coords[:, 0] == b
         idx = (coords[m, 1] + coords[m, 2] * nx + coords[m, 3]).long()
@@ -84,8 +84,9 @@ def shrink_conv(x: Tensor, sd: Dict[str, Tensor], cfg: dict, prefix: str = "shri
 def point_pillar_features(voxel_features, voxel_coords, voxel_num_points, sd, args, n_agents: int,
                           dtype: torch.dtype = torch.float32) -> Tensor:
     """PointPillar.forward up to ``spatial_features_2d`` (point_pillar.py:35-54).  dtype=torch.float64: the same layers in
-    double precision (yardstick of the precision stress tests)."""
-    sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+    double precision (yardstick of the precision stress tests).  Runs on the device of ``voxel_features`` (the weights follow it)."""
+    dev = voxel_features.device
+    sd = {k: (v.to(dev, dtype) if v.is_floating_point() else v.to(dev)) for k, v in sd.items()}
     nx, ny, nz = args["point_pillar_scatter"]["grid_size"]
     pf = pillar_vfe(voxel_features.to(dtype), voxel_num_points, voxel_coords, sd, args["voxel_size"], args["lidar_range"])
     canvas = scatter(pf, voxel_coords, n_agents, int(ny), int(nx))

@@ -31,6 +31,9 @@ What is frozen:
                         attention with relative-position bias, window 8); one down-sampling block of FAXModule.
   g7_pointpillar.npz    PointPillar.forward (features only, eval BN): 2 agents x 400 pillars on a
                         64x48 canvas; PFN output + (2, 256, 12, 16) BEV features.
+  g19_pointpillar_full.npz  PointPillar.forward (features only, eval BN) at the size bench.py's encoder line runs: 5 agents
+                        x 20 000 pillars on a 512 x 512 grid, layer_nums [3, 5, 8] -> (5, 256, 128, 128); sub-sampled as g12
+                        (every 8th row from 3 / every 16th column from 5), rows 0 and 127, per-channel moments.
   g8_decoder.npz        HeteroDecoder.forward (no upsample), 3 samples with ego types 1,0,1, 12x10.
   g9_model.npz          BevformerPointPillarHetero.forward, LiDAR-only batch B=2, record_len [3,2]:
                         pillars -> PointPillar -> regroup -> HeteroFusion -> HeteroDecoder -> psm / rm.
@@ -331,6 +334,28 @@ def g7_pointpillar():
          n_per_agent=np.array(400), pillar_features=pf, out=y)
 
 
+def g19_pointpillar_full():
+    """PointPillar.forward (return_features) at the shipped encoder size: make_args(512, 512, small=False) is the `lidar` part of
+    hmvit_amd.replay.lidar_model_config(512, 512); 5 agents x 20 000 pillars -> (5, 256, 128, 128), stored in the g12 layout."""
+    import time
+    from opencood.models.point_pillar import PointPillar
+    nx = ny = 512
+    args = PO.make_args(nx, ny, small=False)
+    net = PointPillar(args).eval()
+    net.set_return_features()
+    net.load_state_dict(PO.random_state_dict(args, seed=191), strict=True)
+    vf, vc, vn = PO.synthetic_pillars(5, 20000, nx, ny, args, seed=192)
+    t0 = time.time()
+    y = net({"processed_lidar": {"voxel_features": vf, "voxel_coords": vc, "voxel_num_points": vn}})
+    print(f"g19_pointpillar_full.npz: reference forward {time.time() - t0:.1f} s on {torch.get_num_threads()} threads")
+    assert y.shape == (5, 256, 128, 128), y.shape
+    y64 = y.double()
+    save("g19_pointpillar_full.npz", seed_weights=191, seed_pillars=192, grid=np.array([nx, ny]), n_agents=np.array(5),
+         n_per_agent=np.array(20000), out_sub=y[:, :, 3::8, 5::16].contiguous(), out_rows=y[:, :, [0, 127], :].contiguous(),
+         chan_mean=y64.mean((0, 2, 3)), chan_absmean=y64.abs().mean((0, 2, 3)),
+         chan_sqmean=(y64 * y64).mean((0, 2, 3)), abs_max=y64.abs().max())
+
+
 def g9_model():
     """BevformerPointPillarHetero.forward on a LiDAR-only batch (the camera branch is never entered;
     BEVFormerWrapper is replaced by an empty module so that the reference class can be constructed)."""
@@ -503,6 +528,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "g18" in sys.argv[1:]:
         g18_fusion_cfg4()
+        sys.exit(0)
+    if "g19" in sys.argv[1:]:
+        g19_pointpillar_full()
         sys.exit(0)
     if "g10" in sys.argv[1:]:
         g10_postprocess()

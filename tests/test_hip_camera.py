@@ -3,7 +3,7 @@ cross-view module with bottlenecks, up-sampling decoder, and the assembled encod
 import pytest
 import torch
 
-from conftest import rel_max_err
+from conftest import p999_err, rel_max_err
 from oracle import camera_oracle as CAM
 
 pytestmark = pytest.mark.gpu
@@ -77,3 +77,83 @@ def test_resnet50_bottleneck_trunk_vs_oracle(precision, tol):
     assert [tuple(o.shape) for o in out] == [tuple(sh[:2]) + (4,) + tuple(sh[3:]) for sh in net.output_shapes]
     for o, r in zip(out, ref):
         assert o.shape == r.shape and rel_max_err(o.cpu(), r) < tol
+
+
+# The shipped camera size (bench.py's camera-encoder line): ResNet-34 on 5 agents x 4 cameras of 512 x 512, 32 x 32 BEV queries,
+# 4 x 4096 joint keys at pyramid level 1 and 4 x 256 at level 3 -> (5, 256, 128, 128).  (rel-max, p99.9) bounds of each agent's
+# planes against float64, rel-max normalised by that agent's own max, for pyramid levels 1 / 3 and the features alike.  Measured on
+# an MI355X (worst agent and output): f32 2.7e-6 / 5.0e-4, split 2.2e-6 / 4.3e-4, f16 1.6e-3 / 0.31 (features 1.4e-3 / 0.29,
+# level 1 1.5e-3 / 0.20).  The fp32-class modes are held to 10 x their rel-max and to the fusion's p99.9; f16 to at most twice
+# the smallest of its three measured figures.
+CAMERA_FULL_SIZE = {"f32": (3e-5, 1e-3), "split": (3e-5, 1e-3), "f16": (2.5e-3, 0.4)}
+_camera_full = {}
+
+
+def _camera_full_case():
+    """Config, seeded weights, cameras and the float64 oracle (pyramid levels 1 / 3 and the encoder's features), computed once
+    on the GPU for the precisions that follow."""
+    if not _camera_full:
+        from hmvit_amd import synthetic
+        cfg = synthetic.camera_config(image=512, num_layers=34, bev_h=256, bev_w=256)
+        sd = CAM.random_state_dict(cfg, seed=41)
+        batch = synthetic.synthetic_cameras(5, 512, seed=42)
+        sd64 = {k: v.cuda().double() for k, v in sd.items()}
+        b64 = {k: batch[k].cuda().double() for k in ("camera", "intrinsic", "extrinsic")}
+        pyramid = CAM.resnet_encoder(b64["camera"][None], sd64, cfg["encoder"], prefix="encoder.encoder")
+        feats = CAM.camera_encoder(b64, sd64, cfg)
+        _camera_full.update(cfg=cfg, sd=sd, batch=_cuda(batch), pyramid=[f.cpu() for f in pyramid], truth=feats.cpu(), rel={})
+        del sd64, b64, pyramid, feats
+        torch.cuda.empty_cache()
+    return _camera_full
+
+
+def _per_agent(y, ref):
+    return [(rel_max_err(y[a], ref[a]), p999_err(y[a], ref[a])) for a in range(ref.shape[0])]
+
+
+def _camera_full_forward(c, precision):
+    """Pyramid and features of the HIP encoder in `precision`; per-agent (rel-max, p99.9) of levels 1 / 3 and of the features."""
+    from hmvit_amd.camera import CvtCameraEncoder
+    net = CvtCameraEncoder(c["cfg"], precision=precision)
+    missing, unexpected = net.load_state_dict(c["sd"], strict=False)
+    assert not unexpected and all("num_batches_tracked" in k for k in missing), (missing, unexpected)
+    net = net.cuda().eval()
+    net.set_return_features()
+    pyramid = [o.cpu() for o in net.encoder(c["batch"]["camera"][None])]
+    assert [o.shape for o in pyramid] == [r.shape for r in c["pyramid"]]
+    errs = {f"resnet level {lv}": _per_agent(o[0], r[0]) for lv, o, r in zip((1, 3), pyramid, c["pyramid"])}
+    del pyramid
+    y = net(c["batch"]).cpu()
+    assert y.shape == c["truth"].shape == (5, 256, 128, 128)
+    errs["features"] = _per_agent(y, c["truth"])
+    c["rel"][precision] = max(e for e, _ in errs["features"])
+    return net, errs
+
+
+@pytest.mark.parametrize("precision", ["f32", "split", "f16"])
+def test_camera_encoder_full_size_vs_float64(precision):
+    """CvtCameraEncoder at the shipped size against float64, agent by agent: the ResNet-34 pyramid (levels 1 and 3: the row-packed
+    7 x 7 stem on 20 images, the trunk's convolution paths) apart from the features (cross-view attention with a 16 384-key joint
+    softmax, bottlenecks, decoder).  Split is held to the exact-f32 mode's error (4 x + 1e-6).  Asserts that the intended
+    attention path ran: the split-product core in `split`, the f16 block in `f16`."""
+    c = _camera_full_case()
+    net, errs = _camera_full_forward(c, precision)
+    q_tokens = net.cvm.bev_embedding.learned_features[0].numel()
+    for cv in net.cvm.cross_views:
+        att = cv.cross_attend
+        if precision == "split":
+            assert att.precision == "f32" and att._split_core_in_range()
+        if precision == "f16":
+            assert att.precision == "f16" and q_tokens % 64 == 0 and (cv.feat_height * cv.feat_width) % 64 == 0 and cv.dim % 64 == 0
+    del net
+    torch.cuda.empty_cache()
+    rel_b, p999_b = CAMERA_FULL_SIZE[precision]
+    for what, per_agent in errs.items():
+        for a, (e, p) in enumerate(per_agent):
+            print(f"full-size[camera:{precision}] {what} agent {a} vs float64: rel-max {e:.2e} p99.9 {p:.2e}")
+    for what, per_agent in errs.items():
+        assert all(e < rel_b for e, _ in per_agent) and all(p < p999_b for _, p in per_agent), (what, per_agent)
+    if precision == "split":
+        if "f32" not in c["rel"]:
+            _camera_full_forward(c, "f32")
+        assert c["rel"]["split"] <= 4 * c["rel"]["f32"] + 1e-6, c["rel"]

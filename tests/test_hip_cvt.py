@@ -53,7 +53,8 @@ def test_cross_view_attention_level2_size_vs_oracle(precision, tol):
         net(x, bev, feat, I_inv, E_inv)          # CPU tensors: no fallback
 
 
-@pytest.mark.parametrize("b,n,Q,K,heads", [(1, 1, 64, 64, 1), (2, 3, 128, 192, 4), (1, 4, 1024, 1024, 4)])
+@pytest.mark.parametrize("b,n,Q,K,heads", [(1, 1, 64, 64, 1), (2, 3, 128, 192, 4), (1, 4, 1024, 1024, 4),
+                                           (2, 4, 1024, 4096, 4)])     # the shipped level-1 lift: 4 x 4096 joint keys
 def test_cross_attention_core_f16_vs_torch(b, n, Q, K, heads):
     """Matrix-core attention core against a torch f32 evaluation of the same f16 operands (joint softmax over the cameras'
     keys, cvt_modules.py:148-158); logits spread over several units so the running-max rescale is exercised."""
@@ -80,7 +81,7 @@ def test_cross_attention_core_f16_vs_torch(b, n, Q, K, heads):
 
 
 @pytest.mark.parametrize("b,n,Q,K,heads,spread", [(1, 1, 64, 64, 1, 1.5), (2, 3, 128, 192, 4, 1.5), (1, 4, 1024, 1024, 4, 3.0),
-                                                 (2, 2, 64, 200, 2, 1.5)])
+                                                 (2, 2, 64, 200, 2, 1.5), (2, 4, 1024, 4096, 4, 3.0)])
 def test_cross_attention_core_split_vs_float64(b, n, Q, K, heads, spread):
     """HMVIT_PREC_SPLIT: the split-f16 matrix-core kernel (f32 operands as hi + lo halves, three products each) against a float64
     evaluation of the joint softmax over the cameras' keys (cvt_modules.py:148-158), at fp32 round-off class and no worse than the
@@ -93,11 +94,13 @@ def test_cross_attention_core_split_vs_float64(b, n, Q, K, heads, spread):
     q = torch.randn(b, n, Q, hd, generator=gen) * spread
     k = torch.randn(b, n, K, hd, generator=gen) * spread
     v = torch.randn(b, n * K, hd, generator=gen) * 2.0
-    qd = q.double().reshape(b, n, Q, heads, 32).permute(0, 3, 1, 2, 4)
-    kd = k.double().reshape(b, n, K, heads, 32).permute(0, 3, 1, 2, 4)
+    dev = "cuda" if n * K >= 16384 else "cpu"        # the shipped key count: its 1 GB float64 score tensor is built on the GPU
+    qd = q.to(dev).double().reshape(b, n, Q, heads, 32).permute(0, 3, 1, 2, 4)
+    kd = k.to(dev).double().reshape(b, n, K, heads, 32).permute(0, 3, 1, 2, 4)
     dot = (32 ** -0.5) * torch.einsum("bmnqd,bmnkd->bmnqk", qd, kd)
     att = dot.permute(0, 1, 3, 2, 4).reshape(b, heads, Q, n * K).softmax(-1)
-    ref = torch.einsum("bmqk,bkmd->bqmd", att, v.double().reshape(b, n * K, heads, 32)).reshape(b, Q, hd)
+    ref = torch.einsum("bmqk,bkmd->bqmd", att, v.to(dev).double().reshape(b, n * K, heads, 32)).reshape(b, Q, hd).cpu()
+    del qd, kd, dot, att
     qc, kc, vc = q.cuda(), k.cuda(), v.cuda()
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     outs = {}

@@ -110,6 +110,27 @@ def test_g7_pointpillar_encoder():
     assert rel_max_err(y, g["out"]) < TOL
 
 
+def test_g19_pointpillar_encoder_full_size():
+    """The oracle against the reference's PointPillar at the size bench.py's encoder line runs (5 agents x 20 000 pillars,
+    512 x 512 grid, layer_nums [3, 5, 8] -> (5, 256, 128, 128)): sub-grid, rows 0 / 127 and channel moments of g19."""
+    from oracle import pointpillar_oracle as PO
+    g = load_golden("g19_pointpillar_full.npz")
+    nx, ny = [int(v) for v in g["grid"]]
+    args = PO.make_args(nx, ny, small=False)
+    sd = PO.random_state_dict(args, g["seed_weights"])
+    vf, vc, vn = PO.synthetic_pillars(int(g["n_agents"]), int(g["n_per_agent"]), nx, ny, args, int(g["seed_pillars"]))
+    y = PO.point_pillar_features(vf, vc, vn, sd, args, int(g["n_agents"]))
+    assert y.shape == (5, 256, 128, 128)
+    scale = float(g["abs_max"])
+    assert abs(float(y.abs().max()) - scale) <= TOL * scale
+    assert float((y[:, :, 3::8, 5::16] - g["out_sub"]).abs().max()) / scale < TOL
+    assert float((y[:, :, [0, 127], :] - g["out_rows"]).abs().max()) / scale < TOL
+    y64 = y.double()
+    assert float((y64.mean((0, 2, 3)) - g["chan_mean"]).abs().max()) / scale < TOL
+    assert float((y64.abs().mean((0, 2, 3)) - g["chan_absmean"]).abs().max()) / scale < TOL
+    assert float(((y64 * y64).mean((0, 2, 3)) - g["chan_sqmean"]).abs().max() / g["chan_sqmean"].max()) < 2 * TOL
+
+
 def test_g8_hetero_decoder():
     import numpy as np
     from oracle import decoder_oracle as DO
