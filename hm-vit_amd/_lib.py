@@ -99,6 +99,9 @@ _SIGNATURES = {
     "hmvit_bn_train_stats_centered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hmvit_bn_train_apply": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hmvit_bn_train_backward": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hmvit_pointpillar_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "hmvit_pointpillar_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 5 + [C.c_void_p] * 4 +
+                               [C.c_size_t, C.c_void_p]),
     "hmvit_pack_small": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hmvit_nchw_to_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -11,6 +11,8 @@ without ``--fix_lidar_backbone``).  Same layer sequence as the inference path (`
                                                            convolutions, each followed by BatchNorm2d (eps 1e-3) + ReLU
                                                            [``tail_train.Conv3x3`` / ``Deconv`` / ``BnRelu``], channel concat
   DownsampleConv         ``downsample_conv.py:20-51``      3x3 stride-2 + ReLU, 3x3 + ReLU (bias, no norm)
+  cls_head / reg_head    ``point_pillar.py:56-62``         1x1 convolutions [``tail_train.Conv1x1``] - the standalone detector
+                                                           only (without ``set_return_features()``)
 
 Every multiply-accumulate over pixels / points runs in libhmvit (f32 maps, split-f16 products); layout changes, zero
 insertion, concatenation, max and scatter are torch tensor plumbing on the autograd tape.
@@ -20,7 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .tail_train import BnRelu, Conv3x3, _stream, bn_relu_module
+from .tail_train import BnRelu, Conv1x1, Conv3x3, _stream, bn_relu_module
 
 
 class Deconv(torch.autograd.Function):
@@ -110,9 +112,17 @@ def pfn_features(vf, vc, vn, voxel_size, lidar_range):
 
 
 def pointpillar_train_forward(net, data_dict):
-    """``PointPillar.forward`` (features only: the HM-ViT model calls it after ``set_return_features()``) in training mode."""
-    if not net.return_features:
-        raise NotImplementedError("PointPillar in training mode: the feature path (set_return_features()) is built")
+    """``PointPillar.forward`` in training mode: the shrunk feature map (N, C, H, W) after ``set_return_features()`` (the HM-ViT
+    model's LiDAR branch), otherwise the standalone detector's ``{'psm' (N, A, H, W), 'rm' (N, 7 A, H, W)}`` from the 1x1
+    ``cls_head`` / ``reg_head`` (``point_pillar.py:56-62``; the LiDAR backbone pretraining of ``point_pillar_late_fusion.yaml``).
+
+    The detector trains in the arithmetic its training layers implement, precision ``"split"`` (the constructor default: f32 maps,
+    products on split-f16 operands).  A detector built with ``"f32"`` (exact-f32 products) or ``"f16"`` is refused in training mode
+    rather than trained in an arithmetic other than the one it was built with; the feature path keeps its behaviour."""
+    if not net.return_features and net.precision != "split":
+        raise NotImplementedError(f"PointPillar detector in training mode: built with precision {net.precision!r}; the training "
+                                  f"layers run precision 'split' (the default) - construct PointPillar(args) or "
+                                  f"PointPillar(args, precision='split') to train it")
     lidar = data_dict["processed_lidar"]
     vf = lidar["voxel_features"].detach().float().contiguous()
     vc = lidar["voxel_coords"].detach().long()
@@ -156,4 +166,10 @@ def pointpillar_train_forward(net, data_dict):
                 raise NotImplementedError("shrink header in training mode: 3x3 convolutions with padding 1")
             x = torch.relu(Conv3x3.apply(x, c0.weight, c0.bias, c0.stride[0]))
             x = torch.relu(Conv3x3.apply(x, c1.weight, c1.bias, 1))
-    return x.permute(0, 3, 1, 2).contiguous()
+    if net.return_features:
+        return x.permute(0, 3, 1, 2).contiguous()
+
+    # ---- detection heads (1x1 convolutions: hmvit_linear forward / data gradient, hmvit_gemm_tn weight and bias gradient) ----
+    psm = Conv1x1.apply(x, net.cls_head.weight, net.cls_head.bias)
+    rm = Conv1x1.apply(x, net.reg_head.weight, net.reg_head.bias)
+    return {"psm": psm.permute(0, 3, 1, 2).contiguous(), "rm": rm.permute(0, 3, 1, 2).contiguous()}

@@ -4,8 +4,9 @@ Mirror of ``opencood/models/point_pillar.py:9-62``: same constructor ``args`` di
 ``set_return_features()`` / ``forward(data_dict)`` contract (``data_dict['processed_lidar']`` with
 ``voxel_features (Nv, 32, 4)``, ``voxel_coords (Nv, 4) [agent, z, y, x]``, ``voxel_num_points (Nv)``),
 same ``state_dict`` key names, so ``self.lidar_encoder = PointPillar(config['lidar'])`` in
-``bevformer_point_pillar_hetero.py:56`` works unchanged.  Eval mode only (BatchNorm running
-statistics are folded into the convolutions); no CPU path.
+``bevformer_point_pillar_hetero.py:56`` works unchanged.  The kernels below serve eval mode (BatchNorm running
+statistics are folded into the convolutions); train mode runs hm-vit_amd/encoder_train.py, the feature map after
+``set_return_features()`` and ``{'psm', 'rm'}`` of the standalone detector otherwise; no CPU path.
 
 Kernels (csrc/enc.hip): PFN + scatter in one HBM-bound pass, every Conv2d / ConvTranspose2d as an
 MFMA implicit GEMM on NHWC maps; ``torch.cat`` of the three up-sampled maps is free (each deconv

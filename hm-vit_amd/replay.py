@@ -11,6 +11,7 @@ With random weights the AP is that of an untrained detector; what the harness pr
 to load a reference checkpoint (``--checkpoint``: a ``state_dict`` file, loaded ``strict=False`` as ``train_utils.py:66-70``).
 
     python -m hmvit_amd.replay --scenes 8 --precision f16        (from the repository root)
+    python -m hmvit_amd.replay --late --small --checkpoint runs/stage1/net_epoch2.pth     (a stage-1 detector, late fusion)
 """
 from __future__ import annotations
 
@@ -60,7 +61,8 @@ def postprocess_params(cfg: dict) -> dict:
 
 class SyntheticReplayDataset:
     """``len(ds)`` frames; ``ds[i]`` -> {'clouds': [(n_i, 4) float32 per agent], 'pairwise_t_matrix' (1, L, L, 4, 4),
-    'mode' (1, L), 'record_len' (1,), 'object_bbx_corners' (n_obj, 8, 3)} - what the driver needs from ``batch['ego']``."""
+    'mode' (1, L), 'record_len' (1,), 'object_bbx_corners' (n_obj, 8, 3), 'lidar_poses' (L, 4, 4) float64 agent -> ego} - what the
+    driver needs from ``batch['ego']``."""
 
     def __init__(self, cfg: dict, n_frames: int, n_agents: int | None = None, n_obj: int = 12, seed: int = 7):
         self.cfg, self.n_frames, self.n_obj = cfg, n_frames, n_obj
@@ -97,12 +99,16 @@ class SyntheticReplayDataset:
             clouds.append(np.concatenate([local, rs.uniform(0, 1, (len(local), 1))], 1).astype(np.float32))
         return {"clouds": clouds, "pairwise_t_matrix": S.pairwise_from_poses(poses, self.cfg["max_cav"])[None],
                 "mode": torch.ones(1, self.cfg["max_cav"], dtype=torch.float64), "record_len": torch.tensor([L]),
-                "object_bbx_corners": boxes_to_corners_3d(boxes), "object_bbx_center_valid": boxes}
+                "object_bbx_corners": boxes_to_corners_3d(boxes), "object_bbx_center_valid": boxes,
+                "lidar_poses": torch.stack(poses).numpy()}
 
 
-def inference(model, dataset, pre, post, calibrate_top: int | None = 200, log=None) -> dict:
+def inference(model, dataset, pre, post, calibrate_top: int | None = 200, log=None, late: bool = False) -> dict:
     """The driver loop.  ``calibrate_top``: with an untrained head every anchor fires, so the score threshold of each frame
-    is set to keep that many anchors (None: the config's threshold, for a trained checkpoint)."""
+    is set to keep that many anchors (None: the config's threshold, for a trained checkpoint).  ``late``: ``model`` is the
+    standalone ``PointPillar`` detector; every agent's cloud goes through it in its own frame (one batch of L samples) and
+    ``post_process`` projects each agent's boxes with its agent -> ego ``transformation_matrix`` before the joint NMS
+    (``inference_camera.py --fusion_method late``, ``late_fusion_dataset.py`` ``post_process``)."""
     from .postprocess import calculate_ap, caluclate_tp_fp
     dev = next(model.parameters()).device
     anchors = post.generate_anchor_box()
@@ -112,8 +118,11 @@ def inference(model, dataset, pre, post, calibrate_top: int | None = 200, log=No
     for i in range(len(dataset)):
         frame = dataset[i]
         lidar = pre.collate_batch([pre.preprocess(c) for c in frame["clouds"]])
-        batch = {"mode": frame["mode"].to(dev), "record_len": frame["record_len"].to(dev),
-                 "pairwise_t_matrix": frame["pairwise_t_matrix"].to(dev), "processed_lidar": lidar}
+        if late:
+            batch = {"processed_lidar": lidar, "n_agents": len(frame["clouds"])}
+        else:
+            batch = {"mode": frame["mode"].to(dev), "record_len": frame["record_len"].to(dev),
+                     "pairwise_t_matrix": frame["pairwise_t_matrix"].to(dev), "processed_lidar": lidar}
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         out = model(batch)
@@ -125,8 +134,14 @@ def inference(model, dataset, pre, post, calibrate_top: int | None = 200, log=No
             k = max(1, out["psm"].numel() - calibrate_top)
             kth = float(torch.sigmoid(out["psm"].float()).flatten().kthvalue(k).values)
             post.params["target_args"]["score_threshold"] = float(np.nextafter(np.float32(min(kth, 1.0)), np.float32(0)))
-        data = {"ego": {"anchor_box": torch.from_numpy(anchors), "transformation_matrix": torch.eye(4)}}
-        boxes, scores = post.post_process(data, {"ego": {"psm": out["psm"], "rm": out["rm"]}})
+        if late:
+            poses = torch.from_numpy(frame["lidar_poses"]).float()
+            data = {i: {"anchor_box": torch.from_numpy(anchors), "transformation_matrix": poses[i]} for i in range(len(poses))}
+            heads = {i: {"psm": out["psm"][i:i + 1], "rm": out["rm"][i:i + 1]} for i in range(len(poses))}
+        else:
+            data = {"ego": {"anchor_box": torch.from_numpy(anchors), "transformation_matrix": torch.eye(4)}}
+            heads = {"ego": {"psm": out["psm"], "rm": out["rm"]}}
+        boxes, scores = post.post_process(data, heads)
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         gt = torch.from_numpy(frame["object_bbx_corners"]).to(dev)
@@ -154,16 +169,23 @@ def main(argv=None):
                     help="pillar grid (0.4 m cells); boxes outside the evaluation range |y| <= 40 m (GT_RANGE) are dropped "
                          "by the post-processor as in the reference, so the default keeps the map inside it")
     ap.add_argument("--precision", default="f16", choices=["f16", "f32"])
+    ap.add_argument("--small", action="store_true", help="PointPillar layer_nums [1, 2, 2] (as the trainer's --small)")
     ap.add_argument("--checkpoint", default=None, help="state_dict file of the reference model (loaded strict=False)")
+    ap.add_argument("--late", action="store_true",
+                    help="late fusion: the standalone PointPillar detector per agent (a --stage lidar_backbone checkpoint of "
+                         "hmvit_amd.trainer), boxes projected to the ego and merged by the NMS")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
-    from . import BevformerPointPillarHetero, SpVoxelPreprocessor, VoxelPostprocessor
+    from . import BevformerPointPillarHetero, PointPillar, SpVoxelPreprocessor, VoxelPostprocessor
     if not torch.cuda.is_available():
         raise SystemExit("hm-vit_amd has no CPU path: this needs an MI355X")
-    cfg = lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents)
+    cfg = lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents, small=args.small)
     torch.manual_seed(args.seed)
-    model = BevformerPointPillarHetero(cfg, precision=args.precision)
+    if args.late:
+        model = PointPillar(cfg["lidar"], precision=args.precision)
+    else:
+        model = BevformerPointPillarHetero(cfg, precision=args.precision)
     if args.checkpoint:
         missing, unexpected = model.load_state_dict(torch.load(args.checkpoint, map_location="cpu"), strict=False)
         print(f"checkpoint: {len(missing)} missing / {len(unexpected)} unexpected keys")
@@ -178,8 +200,9 @@ def main(argv=None):
     pre = SpVoxelPreprocessor(preprocess_params(cfg), train=False)
     post = VoxelPostprocessor(postprocess_params(cfg), train=False)
     ds = SyntheticReplayDataset(cfg, args.scenes, n_agents=args.agents, seed=args.seed + 7)
-    res = inference(model, ds, pre, post, calibrate_top=None if args.checkpoint else 200, log=print if args.verbose else None)
-    res.update(precision=args.precision, agents=args.agents, grid=args.grid)
+    res = inference(model, ds, pre, post, calibrate_top=None if args.checkpoint else 200, log=print if args.verbose else None,
+                    late=args.late)
+    res.update(precision=args.precision, agents=args.agents, grid=args.grid, fusion="late" if args.late else "intermediate")
     print(json.dumps(res))
 
 

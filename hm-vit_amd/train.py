@@ -12,7 +12,7 @@ Here the fusion's forward and backward are HIP kernels (csrc/capi_train.hip, csr
 (relation matrices into the K / V projections, the bias table into MFMA fragments, hm-vit_amd/weights.py) stay on the autograd
 tape as small tensor algebra, so the kernels' gradients with respect to the folded tensors reach the reference's parameters
 (``relation_att``, ``k_linears`` ...) by ordinary autograd.  The loss is plain elementwise torch (kept in
-PyTorch), the optimiser is ``torch.optim.AdamW`` as in the reference, the gradient all-reduce is torch's
+PyTorch); ``FusedPointPillarLoss`` is the same loss with its gradient in one HIP kernel pair (csrc/loss.hip), opt-in.  The optimiser is ``torch.optim.AdamW`` as in the reference, the gradient all-reduce is torch's
 ``DistributedDataParallel`` over RCCL ("nccl") exactly as ``train_camera.py`` wraps the model.
 """
 from __future__ import annotations
@@ -318,6 +318,62 @@ class PointPillarLoss(torch.nn.Module):
         loc = torch.where(n < self.beta, 0.5 * n ** 2 / self.beta, n - 0.5 * self.beta)
         reg_loss = (loc * reg_weights.unsqueeze(-1)).sum() / B * self.reg_coe
         total = reg_loss + conf_loss
+        self.loss_dict = {"total_loss": total, "reg_loss": reg_loss, "conf_loss": conf_loss}
+        return total
+
+
+class PointPillarLossFunction(torch.autograd.Function):
+    """(conf_loss, reg_loss, total) of ``PointPillarLoss`` from ``hmvit_pointpillar_loss`` (csrc/loss.hip), which also writes
+    d total / d psm and d total / d rm in the forward; the backward scales them by the incoming gradient of ``total`` (conf_loss
+    and reg_loss are reported values, not differentiable outputs)."""
+
+    @staticmethod
+    def forward(ctx, psm, rm, pos_equal_one, targets, params):
+        cls_weight, reg_coe, alpha, gamma, beta = params
+        dev = psm.device
+        if dev.type != "cuda":
+            raise RuntimeError("hm-vit_amd runs on the GPU only (HIP kernels, no CPU fallback)")
+        B, A, H, W = psm.shape
+        if tuple(rm.shape) != (B, 7 * A, H, W):
+            raise ValueError(f"rm must be {(B, 7 * A, H, W)}, got {tuple(rm.shape)}")
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        psm, rm = f32(psm), f32(rm)
+        lab = f32(pos_equal_one).view(B, H, W, A)
+        tg = f32(targets).view(B, H, W, 7 * A)
+        need = _lib.lib.hmvit_pointpillar_loss_workspace_bytes(B, H, W)
+        if need == 0:
+            _lib.check(-22, "hmvit_pointpillar_loss_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
+        dpsm, drm = torch.empty_like(psm), torch.empty_like(rm)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib.hmvit_pointpillar_loss(
+                psm.data_ptr(), rm.data_ptr(), lab.data_ptr(), tg.data_ptr(), B, H, W, A, float(cls_weight), float(reg_coe),
+                float(alpha), float(gamma), float(beta), loss3.data_ptr(), dpsm.data_ptr(), drm.data_ptr(), ws.data_ptr(), need,
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "hmvit_pointpillar_loss")
+        ctx.grads = (dpsm, drm)
+        conf, reg, total = loss3[0], loss3[1], loss3[2]
+        ctx.mark_non_differentiable(conf, reg)
+        ctx.set_materialize_grads(False)          # no zero tensors for the two reported values
+        return conf, reg, total
+
+    @staticmethod
+    def backward(ctx, _dconf, _dreg, dtotal):
+        dpsm, drm = ctx.grads
+        ctx.grads = None
+        if dtotal is None:
+            return None, None, None, None, None
+        return dpsm * dtotal, drm * dtotal, None, None, None
+
+
+class FusedPointPillarLoss(PointPillarLoss):
+    """``PointPillarLoss`` with the forward and the gradient in one HIP kernel pair (csrc/loss.hip): same constructor dict, call
+    signature, return value and ``loss_dict``; the autograd tape holds one node instead of the ~25 elementwise ops."""
+
+    def forward(self, output_dict: Dict[str, torch.Tensor], target_dict: Dict[str, torch.Tensor]):
+        params = (self.cls_weight, self.reg_coe, self.alpha, self.gamma, self.beta)
+        conf_loss, reg_loss, total = PointPillarLossFunction.apply(output_dict["psm"], output_dict["rm"],
+                                                                   target_dict["pos_equal_one"], target_dict["targets"], params)
         self.loss_dict = {"total_loss": total, "reg_loss": reg_loss, "conf_loss": conf_loss}
         return total
 

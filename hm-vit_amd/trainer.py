@@ -25,8 +25,15 @@ on libhmvit too (``--train_lidar_backbone``, hm-vit_amd/encoder_train.py);
 the detection tail (``HeteroDecoder``: four 3x3 convolutions + BatchNorm in batch-statistics mode + ReLU + two 1x1 heads) runs
 HIP forward and backward kernels as well (hm-vit_amd/tail_train.py).
 
+The two stages of the reference's recipe: stage 1 (``--stage lidar_backbone``, ``opcl/point_pillar_late_fusion.yaml``) trains the
+standalone PointPillar detector on single-agent samples (``LateFusionTrainDataset``: one random agent per frame, in its own frame,
+``late_fusion_dataset.py:33-49``) with ``FusedPointPillarLoss``; stage 2 (the default ``--stage hetero``) loads that checkpoint into
+``model.lidar_encoder`` (``--lidar_backbone_dir``, ``train_camera.py:109-114``) and freezes it.
+
     python -m hmvit_amd.trainer --epochs 2 --frames 8                      (one GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m hmvit_amd.trainer --epochs 2
+    python -m hmvit_amd.trainer --stage lidar_backbone --model_dir runs/stage1          (stage 1)
+    python -m hmvit_amd.trainer --lidar_backbone_dir runs/stage1 --model_dir runs/stage2 (stage 2)
 """
 from __future__ import annotations
 
@@ -42,7 +49,7 @@ import numpy as np
 import torch
 
 from . import replay as R
-from .train import PointPillarLoss, make_optimizer
+from .train import FusedPointPillarLoss, PointPillarLoss, make_optimizer
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -87,9 +94,12 @@ def default_hypes(epoches: int = 2) -> dict:
 
 
 def create_loss(hypes: dict):
+    """``point_pillar_loss``: the elementwise torch ``PointPillarLoss``, or with ``hypes['loss']['fused']`` the same loss as one HIP
+    kernel pair (``FusedPointPillarLoss``)."""
     if hypes["loss"]["core_method"] != "point_pillar_loss":
         raise NotImplementedError(f"loss {hypes['loss']['core_method']}: only point_pillar_loss is built")
-    return PointPillarLoss(hypes["loss"]["args"])
+    cls = FusedPointPillarLoss if hypes["loss"].get("fused", False) else PointPillarLoss
+    return cls(hypes["loss"]["args"])
 
 
 def setup_optimizer(hypes: dict, model):
@@ -191,6 +201,71 @@ class SyntheticTrainDataset(R.SyntheticReplayDataset):
         return frame
 
 
+def cav_frame_boxes(boxes: np.ndarray, pose: np.ndarray) -> np.ndarray:
+    """(n, 7) [x, y, z, h, w, l, yaw] boxes of the ego frame -> the frame of the agent whose agent -> ego pose is ``pose`` (4, 4):
+    centre by the inverse pose, yaw minus the pose's yaw (wrapped to [-pi, pi))."""
+    b = np.asarray(boxes, np.float64).copy()
+    inv = np.linalg.inv(np.asarray(pose, np.float64))
+    b[:, 0:3] = b[:, 0:3] @ inv[:3, :3].T + inv[:3, 3]
+    yaw = b[:, 6] - math.atan2(pose[1, 0], pose[0, 0])
+    b[:, 6] = (yaw + math.pi) % (2 * math.pi) - math.pi
+    return b.astype(np.float32)
+
+
+class LateFusionTrainDataset(R.SyntheticReplayDataset):
+    """The training side of ``CamLiLateFusionDataset`` (``mixed/late_fusion_dataset.py:33-49``) on the synthetic frames: sample
+    ``i`` is ONE agent of frame ``i``, drawn with a seeded generator, in that agent's own frame - its point cloud as it sees it, the
+    boxes moved into its frame (``cav_frame_boxes``) and kept when their centre lies inside its range (the reference's
+    ``mask_boxes_outside_range_numpy``), padded to ``max_num``, and the ``generate_label`` targets of its anchors."""
+
+    def __init__(self, cfg, n_samples, post, n_agents=None, n_obj=12, seed=7, max_num=100):
+        super().__init__(cfg, n_samples, n_agents=n_agents, n_obj=n_obj, seed=seed)
+        self.post, self.max_num = post, max_num
+        self.anchors = post.generate_anchor_box()
+
+    def pick_cav(self, idx) -> int:
+        return int(np.random.RandomState(self.seed + 13 + 1000 * idx).randint(self.n_agents))
+
+    def __getitem__(self, idx):
+        frame = super().__getitem__(idx)
+        cav = self.pick_cav(idx)
+        pose = frame["lidar_poses"][cav]
+        boxes = cav_frame_boxes(frame["object_bbx_center_valid"], pose)
+        rng = self.cfg["lidar"]["lidar_range"]
+        keep = np.nonzero((boxes[:, 0] > rng[0]) & (boxes[:, 0] < rng[3]) & (boxes[:, 1] > rng[1]) & (boxes[:, 1] < rng[4]))[0]
+        keep = keep[: self.max_num]
+        center = np.zeros((self.max_num, 7), np.float32)
+        mask = np.zeros(self.max_num, np.float32)
+        center[: len(keep)], mask[: len(keep)] = boxes[keep], 1
+        label = self.post.generate_label(gt_box_center=center, anchors=self.anchors, mask=mask)
+        return {"cloud": frame["clouds"][cav], "cav": cav, "lidar_pose": pose, "object_ids": keep, "object_bbx_center": center,
+                "object_bbx_mask": mask, "label_dict": label}
+
+
+class Batched:
+    """``len(ds) / batch`` batches of consecutive samples (the last one shorter), as a ``DataLoader(batch_size=batch)`` without
+    shuffling hands them to ``collate_batch_train``."""
+
+    def __init__(self, ds, batch: int):
+        self.ds, self.batch = ds, max(1, int(batch))
+
+    def __len__(self):
+        return (len(self.ds) + self.batch - 1) // self.batch
+
+    def __getitem__(self, i):
+        return [self.ds[j] for j in range(i * self.batch, min(len(self.ds), (i + 1) * self.batch))]
+
+
+def to_late_batch(samples: list, pre, device) -> dict:
+    """A list of ``LateFusionTrainDataset`` samples -> the standalone detector's batch: every sample's pillars under its own batch
+    index (``collate_batch``), ``n_agents`` = the batch size, and the stacked ``label_dict``."""
+    from .postprocess import VoxelPostprocessor
+    lidar = pre.collate_batch([pre.preprocess(s["cloud"]) for s in samples])
+    label = VoxelPostprocessor.collate_batch([s["label_dict"] for s in samples])
+    return {"processed_lidar": lidar, "n_agents": len(samples),
+            "label_dict": {k: v.to(device=device, dtype=torch.float32) for k, v in label.items()}}
+
+
 def to_batch(frame: dict, pre, device) -> dict:
     """One frame -> the ``batch['ego']`` dict the model and the criterion take (pillarisation on the device, csrc/vox.hip)."""
     lidar = pre.collate_batch([pre.preprocess(c) for c in frame["clouds"]])
@@ -206,7 +281,7 @@ def to_batch(frame: dict, pre, device) -> dict:
 # ---------------------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------------------
-def validate(model, val_dataset, pre, criterion, device) -> float:
+def validate(model, val_dataset, pre, criterion, device, batch_fn=to_batch) -> float:
     """The validation pass of ``train_camera.py:201-220``: ``model.eval()`` per batch, ``torch.no_grad()``, mean of the
     criterion over the validation frames (every rank runs the whole split, as the reference's un-sharded ``val_loader``).
     ``eval()`` flips the swapped-in modules to their inference kernels (BatchNorm running statistics, no dropout, the fused
@@ -215,16 +290,17 @@ def validate(model, val_dataset, pre, criterion, device) -> float:
     with torch.no_grad():
         for i in range(len(val_dataset)):
             model.eval()
-            batch = to_batch(val_dataset[i], pre, device)
+            batch = batch_fn(val_dataset[i], pre, device)
             losses.append(float(criterion(model(batch), batch["label_dict"])))
     return sum(losses) / max(1, len(losses))
 
 
 def train(model, dataset, pre, hypes: dict, saved_path: str | None = None, init_epoch: int = 0, dist_info: dict | None = None,
-          log=None, val_dataset=None) -> dict:
+          log=None, val_dataset=None, batch_fn=to_batch) -> dict:
     """train_camera.py:133-230 (no tensorboard or AMP).  Frames shard over ranks as ``DistributedSampler`` does (rank r takes
     frames r, r + world, ...; the permutation is reseeded per epoch by ``set_epoch``); ``val_dataset``: the validation split,
-    run every ``eval_freq`` epochs (:201-220)."""
+    run every ``eval_freq`` epochs (:201-220).  ``batch_fn(item, pre, device)``: a dataset item -> the model's batch with its
+    ``label_dict`` (``to_batch``; ``to_late_batch`` for the standalone detector of stage 1)."""
     info = dist_info or {"distributed": False, "rank": 0, "world_size": 1, "gpu": 0}
     device = next(model.parameters()).device
     model_without_ddp = model
@@ -243,7 +319,7 @@ def train(model, dataset, pre, hypes: dict, saved_path: str | None = None, init_
         mine = [int(order[(rank + k * world) % len(order)]) for k in range(num_steps)]      # padded like DistributedSampler
         losses = []
         for i, idx in enumerate(mine):
-            batch = to_batch(dataset[idx], pre, device)
+            batch = batch_fn(dataset[idx], pre, device)
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
             model.train()
@@ -264,7 +340,7 @@ def train(model, dataset, pre, hypes: dict, saved_path: str | None = None, init_
                     f"loc {float(criterion.loss_dict['reg_loss']):.4f} lr {optimizer.param_groups[0]['lr']:.2e}")
         history.append(sum(losses) / len(losses))
         if val_dataset is not None and epoch % hypes["train_params"]["eval_freq"] == 0:
-            val = validate(model, val_dataset, pre, criterion, device)
+            val = validate(model, val_dataset, pre, criterion, device, batch_fn)
             val_history.append(val)
             if log:
                 log("At epoch %d, the validation loss is %f" % (epoch, val))
@@ -284,8 +360,25 @@ def train(model, dataset, pre, hypes: dict, saved_path: str | None = None, init_
     return res
 
 
+def build_lidar_backbone(args):
+    """Stage 1 (``point_pillar_late_fusion.yaml``): the standalone PointPillar detector and batches of single-agent samples."""
+    from . import PointPillar, SpVoxelPreprocessor, VoxelPostprocessor
+    cfg = R.lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents, small=args.small)
+    torch.manual_seed(args.seed)
+    model = PointPillar(cfg["lidar"])
+    pre = SpVoxelPreprocessor(R.preprocess_params(cfg), train=True)
+    post = VoxelPostprocessor(R.postprocess_params(cfg), train=True)
+    batch = getattr(args, "batch", 8)
+    ds = Batched(LateFusionTrainDataset(cfg, args.frames, post, n_agents=args.agents, seed=args.seed + 7), batch)
+    val = (Batched(LateFusionTrainDataset(cfg, args.val_frames, post, n_agents=args.agents, seed=args.seed + 100007), batch)
+           if args.val_frames > 0 else None)
+    return cfg, model, pre, post, ds, val
+
+
 def build(args):
     from . import BevformerPointPillarHetero, SpVoxelPreprocessor, VoxelPostprocessor
+    if getattr(args, "stage", "hetero") == "lidar_backbone":
+        return build_lidar_backbone(args)
     cfg = R.lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents, small=args.small)
     torch.manual_seed(args.seed)
     camera_encoder = None
@@ -300,6 +393,11 @@ def build(args):
     model = BevformerPointPillarHetero(cfg, camera_encoder=camera_encoder, precision=args.precision)
     if mixed and not getattr(args, "train_camera_backbone", False):
         model.fix_camera_backbone()                     # train_camera.py --fix_camera_backbone (the default here: faster steps)
+    if getattr(args, "lidar_backbone_dir", None):
+        # train_camera.py:109-114: the stage-1 detector's weights into the LiDAR encoder (same module, same keys)
+        epoch, _ = load_saved_model(args.lidar_backbone_dir, model.lidar_encoder)
+        if epoch == 0:
+            raise FileNotFoundError(f"no net_epoch*.pth in {args.lidar_backbone_dir}")
     if not args.train_lidar_backbone:
         model.fix_lidar_backbone()
     pre = SpVoxelPreprocessor(R.preprocess_params(cfg), train=True)
@@ -328,6 +426,14 @@ def main(argv=None):
     ap.add_argument("--train_lidar_backbone", action="store_true",
                     help="do NOT freeze the LiDAR encoder: PointPillar trains too (hm-vit_amd/encoder_train.py)")
     ap.add_argument("--model_dir", default=None, help="folder with net_epoch%%d.pth to resume from / save into")
+    ap.add_argument("--stage", default="hetero", choices=["hetero", "lidar_backbone"],
+                    help="lidar_backbone: stage 1, the standalone PointPillar detector on single-agent samples "
+                         "(point_pillar_late_fusion.yaml); hetero: the HM-ViT model (stage 2)")
+    ap.add_argument("--batch", type=int, default=8, help="samples per step of --stage lidar_backbone (the yaml's batch_size)")
+    ap.add_argument("--lidar_backbone_dir", default=None,
+                    help="folder with a stage-1 net_epoch%%d.pth: loaded into model.lidar_encoder before it is frozen")
+    ap.add_argument("--fused_loss", action="store_true",
+                    help="the HIP loss kernel pair (FusedPointPillarLoss) instead of the elementwise torch loss in stage 2")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (nccl = RCCL)")
     ap.add_argument("--verbose", action="store_true")
@@ -336,15 +442,21 @@ def main(argv=None):
         raise SystemExit("hm-vit_amd has no CPU path: this needs an MI355X")
     info = init_distributed_mode(args.backend)
     hypes = default_hypes(args.epochs)
+    stage1 = args.stage == "lidar_backbone"
+    if stage1 or args.fused_loss:
+        hypes["loss"]["fused"] = True
     cfg, model, pre, post, ds, val = build(args)
     init_epoch = 0
     if args.model_dir and os.path.exists(args.model_dir):
         init_epoch, model = load_saved_model(args.model_dir, model)
     model = model.to(f"cuda:{info['gpu']}")
     res = train(model, ds, pre, hypes, saved_path=args.model_dir, init_epoch=init_epoch, dist_info=info,
-                log=print if args.verbose and info["rank"] == 0 else None, val_dataset=val)
+                log=print if args.verbose and info["rank"] == 0 else None, val_dataset=val,
+                batch_fn=to_late_batch if stage1 else to_batch)
     if info["rank"] == 0:
-        res.update(agents=args.agents, grid=args.grid, frames=args.frames)
+        res.update(agents=args.agents, grid=args.grid, frames=args.frames, stage=args.stage)
+        if stage1:
+            res.update(batch=args.batch)
         print(json.dumps(res))
     if info["distributed"]:
         import torch.distributed as dist

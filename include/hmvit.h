@@ -334,6 +334,19 @@ int hmvit_bn_train_apply(const float* x, const float* mean, const float* rstd, c
 int hmvit_bn_train_backward(const float* x, const float* y, const float* dy, const float* mean, const float* rstd, const float* gamma,
                             float* sums, float* dx, int M, int C, int relu, void* stream);
 
+/* ---- detector loss (loss/point_pillar_loss.py:68-142) with its gradient, csrc/loss.hip ----
+ * psm (B, A, H, W) and rm (B, 7 A, H, W) as the heads write them (NCHW), pos_equal_one (B, H, W, A) and targets (B, H, W, 7 A) as
+ * VoxelPostprocessor.generate_label / collate_batch produce them, all f32.  Writes loss3[3] = {conf_loss, reg_loss, total} and the
+ * gradient of `total` with respect to psm / rm into dpsm / drm (same layouts, every element written).  Focal loss with logits (alpha,
+ * gamma; the pt^gamma factor is differentiated), normalised per sample by max(1, #positives); smooth-L1 (beta) on the 7 deltas with
+ * sin(p - t) = sin p cos t - cos p sin t on the yaw and NaN targets replaced by the prediction; both sums / B, times cls_weight / reg.
+ * Three launches (positive counts, loss terms + gradients, final sum), fixed-order reductions (no float atomics): bit-identical run
+ * to run, nothing read back.  `workspace`: hmvit_pointpillar_loss_workspace_bytes(B, H, W) bytes. */
+size_t hmvit_pointpillar_loss_workspace_bytes(int B, int H, int W);
+int hmvit_pointpillar_loss(const float* psm, const float* rm, const float* pos_equal_one, const float* targets, int B, int H, int W,
+                           int A, float cls_weight, float reg_coe, float alpha, float gamma, float beta, float* loss3, float* dpsm,
+                           float* drm, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- single operators (used by the parity tests; same kernels as the fused forward) ---- */
 
 /* The small integer inputs of HeteroFusion.forward - mode (B, L), record_len (B), mask (B, L), in whatever dtype the caller holds
