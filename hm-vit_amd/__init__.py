@@ -11,6 +11,7 @@ from .voxelizer import SpVoxelPreprocessor  # noqa: F401
 from .cvt import BEVEmbedding, CrossAttention, CrossViewAttention  # noqa: F401
 from .camera import ResnetEncoder, CrossViewModule, CvtCameraEncoder  # noqa: F401
 from .fax import CrossViewSwapAttention, FAXModule, FaxCameraEncoder  # noqa: F401
+FaxFusedTransformer = FaxCameraEncoder     # the reference's name of the camera detector (fax_fused_transformer.py): the same class
 from .train import PointPillarLoss, FusedPointPillarLoss, make_optimizer, train_step  # noqa: F401  (training: loss / optimiser / one step; loop in .trainer)
 
 # the precision mode that is held to the reference's own fp32 tolerance (1e-4) and that bench.py reports as the headline
@@ -19,4 +20,5 @@ REFERENCE_PRECISION = "split"
 __all__ = ["HeteroFusion", "HeteroFusionBlock", "PointPillar", "HeteroDecoder", "NaiveCompressor", "BevformerPointPillarHetero",
            "VoxelPostprocessor", "quad_iou", "caluclate_tp_fp", "calculate_ap", "voc_ap", "SpVoxelPreprocessor", "BEVEmbedding", "CrossAttention", "CrossViewAttention",
            "ResnetEncoder", "CrossViewModule", "CvtCameraEncoder", "CrossViewSwapAttention", "FAXModule", "FaxCameraEncoder",
+           "FaxFusedTransformer",
            "PointPillarLoss", "FusedPointPillarLoss", "make_optimizer", "train_step"]

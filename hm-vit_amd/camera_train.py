@@ -376,8 +376,9 @@ def cross_view_module_forward(cvm, batch):
     return x.reshape(b, l, *x.shape[1:])
 
 
-def naive_decoder_forward(dec, x_nchw, use_upsample=True):
-    """``NaiveDecoder.forward`` (naive_decoder.py:63-92) on (N, C, H, W): per layer conv - BN - ReLU, nearest x2, conv - BN - ReLU."""
+def naive_decoder_forward(dec, x_nchw, use_upsample=True, nhwc=False):
+    """``NaiveDecoder.forward`` (naive_decoder.py:63-92) on (N, C, H, W): per layer conv - BN - ReLU, nearest x2, conv - BN - ReLU.
+    ``nhwc``: return the map as (N, H, W, C) (for 1x1 heads that read it in that layout)."""
     t = x_nchw.permute(0, 2, 3, 1).contiguous()
     layers = dec.decoder
     for i in range(0, len(layers), 6):
@@ -385,7 +386,7 @@ def naive_decoder_forward(dec, x_nchw, use_upsample=True):
         if use_upsample:
             t = t.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
         t = TT.bn_relu_module(conv3x3(t, layers[i + 3]), layers[i + 4])
-    return t.permute(0, 3, 1, 2).contiguous()
+    return t if nhwc else t.permute(0, 3, 1, 2).contiguous()
 
 
 def cvt_camera_encoder_forward(enc, batch_camera):

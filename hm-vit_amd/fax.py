@@ -327,9 +327,12 @@ class FAXModule(nn.Module):
 
 
 class FaxCameraEncoder(nn.Module):
-    """The camera branch of ``FaxFusedTransformer`` (fax_fused_transformer.py:12-57) for HM-ViT's camera slot.  config:
-    {'encoder': ResnetEncoder params, 'fax': FAXModule config, 'decoder': NaiveDecoder params}; ``forward(batch_camera)`` with
-    'camera' (N, n_cam, H, W, 3), 'intrinsic' (N, n_cam, 3, 3), 'extrinsic' (N, n_cam, 4, 4) -> (N, num_ch_dec[0], Hb, Wb)."""
+    """``FaxFusedTransformer`` (fax_fused_transformer.py:12-64): ResnetEncoder -> FAXModule -> up-sampling NaiveDecoder -> 1x1
+    ``cls_head`` / ``reg_head``.  config: {'encoder': ResnetEncoder params, 'fax': FAXModule config, 'decoder': NaiveDecoder params,
+    'anchor_number'}; ``forward(batch_camera)`` with 'camera' (N, n_cam, H, W, 3), 'intrinsic' (N, n_cam, 3, 3), 'extrinsic'
+    (N, n_cam, 4, 4) -> the standalone camera detector's {'psm' (N, A, Hb, Wb), 'rm' (N, 7 A, Hb, Wb)} (the camera backbone of
+    ``opcl/fax_late_fusion.yaml``), or after ``set_return_features()`` the (N, num_ch_dec[0], Hb, Wb) map of HM-ViT's camera slot.
+    The batch dict is not modified (the reference unsqueezes its entries in place)."""
 
     def __init__(self, config: dict, precision: str = "split"):
         super().__init__()
@@ -338,20 +341,20 @@ class FaxCameraEncoder(nn.Module):
         fax["backbone_output_shape"] = self.encoder.output_shapes
         self.fax = FAXModule(fax, precision=precision)
         self.decoder = NaiveDecoder(config["decoder"])
-        self.cls_head = nn.Conv2d(256, config.get("anchor_number", 2), kernel_size=1)       # present in the reference module, unused
-        self.reg_head = nn.Conv2d(256, 7 * config.get("anchor_number", 2), kernel_size=1)   # when it only returns features
+        self.cls_head = nn.Conv2d(256, config.get("anchor_number", 2), kernel_size=1)
+        self.reg_head = nn.Conv2d(256, 7 * config.get("anchor_number", 2), kernel_size=1)
         self.precision = precision
         self.return_features = False
         self._prep = _Prepared()
+        self._prep_heads = (_Prepared(), _Prepared())
 
     def set_return_features(self):
         self.return_features = True
 
     def forward(self, batch_camera):
-        if not self.return_features:
-            raise NotImplementedError("FaxCameraEncoder serves the HM-ViT camera slot: call set_return_features() first")
         if self.training:
-            # un-frozen camera backbone (train_camera.py:109-120): HIP forward + backward on the autograd tape
+            # un-frozen camera backbone (train_camera.py:109-120) or the detector's own pretraining (fax_late_fusion.yaml): HIP
+            # forward + backward on the autograd tape
             if not torch.is_grad_enabled():
                 raise RuntimeError("hmvit_amd.FaxCameraEncoder: train() mode under no_grad; call eval() for inference")
             from .fax_train import fax_camera_encoder_forward
@@ -368,4 +371,13 @@ class FaxCameraEncoder(nn.Module):
         for i in range(0, len(convs), 2):
             t = convs[i](t)
             t = convs[i + 1](t, up2=True)            # NaiveDecoder.upsample between the two convolutions of a layer
-        return _to_nchw(t, self.decoder.num_ch_dec[0])
+        if self.return_features:
+            return _to_nchw(t, self.decoder.num_ch_dec[0])
+        if t.shape[-1] != self.cls_head.in_channels:
+            raise ValueError(f"FaxCameraEncoder heads read {self.cls_head.in_channels} channels, the decoder gives {t.shape[-1]}")
+        # the heads read the decoder's NHWC map directly: 1x1 convolutions on the same implicit-GEMM kernel (PointPillar's heads)
+        out = {}
+        for name, head, prep in (("psm", self.cls_head, self._prep_heads[0]), ("rm", self.reg_head, self._prep_heads[1])):
+            conv = prep.get(head, prec, lambda: _Conv(head, None, prec, dt))
+            out[name] = _to_nchw(conv(t, relu=False), head.out_channels)
+        return out

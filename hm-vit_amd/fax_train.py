@@ -158,9 +158,16 @@ def fax_module_forward(fm, batch):
 
 
 def fax_camera_encoder_forward(enc, batch_camera):
-    """``FaxCameraEncoder.forward`` in training mode: images -> ResNet pyramid -> FAX lift -> decoder -> (N, num_ch_dec[0], Hb, Wb)."""
+    """``FaxCameraEncoder.forward`` in training mode: images -> ResNet pyramid -> FAX lift -> decoder -> (N, num_ch_dec[0], Hb, Wb)
+    after ``set_return_features()``, otherwise the detector's {'psm', 'rm'} from the 1x1 ``cls_head`` / ``reg_head``
+    (fax_fused_transformer.py:59-64) on ``tail_train.Conv1x1``, as PointPillar's heads train (encoder_train.py)."""
     cam = batch_camera["camera"]
     feats = CT.resnet_encoder_forward(enc.encoder, cam[:, None])
     x = fax_module_forward(enc.fax, {"camera": cam[:, None], "intrinsic": batch_camera["intrinsic"][:, None],
                                      "extrinsic": batch_camera["extrinsic"][:, None], "features": feats})[:, 0]
-    return CT.naive_decoder_forward(enc.decoder, x, use_upsample=True)
+    if enc.return_features:
+        return CT.naive_decoder_forward(enc.decoder, x, use_upsample=True)
+    t = CT.naive_decoder_forward(enc.decoder, x, use_upsample=True, nhwc=True)
+    psm = TT.Conv1x1.apply(t, enc.cls_head.weight, enc.cls_head.bias)
+    rm = TT.Conv1x1.apply(t, enc.reg_head.weight, enc.reg_head.bias)
+    return {"psm": psm.permute(0, 3, 1, 2).contiguous(), "rm": rm.permute(0, 3, 1, 2).contiguous()}

@@ -81,6 +81,48 @@ def camera_config(image: int = 64, num_layers: int = 18, bev_h: int = 32, bev_w:
     return {"encoder": enc, "cvm": cvm, "decoder": {"input_dim": dim, "num_layer": 2, "num_ch_dec": [256, 256]}}
 
 
+def fax_camera_config(nx: int, ny: int, image: int = 64, num_layers: int = 18, meters: float | None = None,
+                      voxel: float = 0.4) -> dict:
+    """The FAX camera detector's config (``FaxCameraEncoder`` / ``FaxFusedTransformer``) with the structure of
+    ``opcl/fax_late_fusion.yaml``'s model block, sized for an (nx, ny) pillar grid and `image` x `image` cameras.
+
+    The head grid is (ny / 4, nx / 4): ``VoxelPostprocessor``'s anchor grid for that pillar grid and the LiDAR feature grid of
+    the HM-ViT model, so the same map serves the detector's heads and the model's camera slot.  BEV queries at (ny / 4, nx / 4) x
+    [1/2, 1/4, 1/8], image features of ResNet levels 1..3 (image / 8, / 16, / 32).  Level i splits both into n_i x n_i windows,
+    the yaml's [8, 4, 1] (it pairs 512-pixel images with a 256 BEV: q windows [16, 16, 32], feature windows [8, 8, 16]), fewer where
+    a feature map is too small for 2 x 2-pixel windows.  ``meters``: the BEV extent (default: the grid's, nx * voxel; the yaml
+    rounds 102.4 m to 100).  Raises ``ValueError`` when the windows cannot tile a grid: the closing self-attention's
+    relative-position table covers a square map, so the grid must be square, and every level must split evenly."""
+    if nx != ny:
+        raise ValueError(f"FAX camera detector: the grid must be square (the self-attention's relative-position bias covers a "
+                         f"square map), got {nx} x {ny}")
+    if image % 32:
+        raise ValueError(f"FAX camera detector: the image size must be a multiple of 32 (ResNet level 3), got {image}")
+    bev = ny // 2
+    if ny % 16:
+        raise ValueError(f"FAX camera detector: the grid must be a multiple of 16 (BEV levels bev / 2 .. bev / 8), got {ny}")
+    q_win, f_win = [], []
+    for i, n_yaml in enumerate((8, 4, 1)):
+        q, f = bev >> (i + 1), image >> (i + 3)
+        n = max(1, min(n_yaml, f // 2))
+        if q % n or f % n:
+            raise ValueError(f"FAX camera detector: level {i} has a {q} x {q} BEV map and a {f} x {f} feature map, which "
+                             f"{n} x {n} windows cannot tile")
+        q_win.append([q // n, q // n])
+        f_win.append([f // n, f // n])
+    m = float(meters) if meters is not None else nx * voxel
+    enc = {"num_layers": num_layers, "pretrained": False, "image_width": image, "image_height": image, "id_pick": [1, 2, 3]}
+    fax = {"dim": [128, 128, 128], "middle": [2, 2, 2],
+           "bev_embedding": {"sigma": 1.0, "bev_height": bev, "bev_width": bev, "h_meters": m, "w_meters": m, "offset": 0.0,
+                             "upsample_scales": [2, 4, 8]},
+           "cross_view": {"image_height": image, "image_width": image, "no_image_features": False, "skip": True, "heads": [4, 4, 4],
+                          "dim_head": [32, 32, 32], "qkv_bias": True},
+           "cross_view_swap": {"rel_pos_emb": False, "q_win_size": q_win, "feat_win_size": f_win,
+                               "bev_embedding_flag": [True, False, False]},
+           "self_attn": {"dim_head": 32, "dropout": 0.1, "window_size": bev // 8}}
+    return {"anchor_number": 2, "encoder": enc, "fax": fax, "decoder": {"input_dim": 128, "num_layer": 2, "num_ch_dec": [256, 256]}}
+
+
 def synthetic_cameras(n_agents: int, image: int, seed: int = 0) -> dict:
     """``camera`` (N, 4, image, image, 3) ~ N(0, 1) (the dataset hands over ImageNet-normalised RGB, ``rgb_preprocessor.py:16-30``),
     ``intrinsic`` (N, 4, 3, 3) with the focal length of the reference's test yaml (335.64 px at 800 px, rescaled) and

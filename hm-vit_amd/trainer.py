@@ -27,13 +27,16 @@ HIP forward and backward kernels as well (hm-vit_amd/tail_train.py).
 
 The two stages of the reference's recipe: stage 1 (``--stage lidar_backbone``, ``opcl/point_pillar_late_fusion.yaml``) trains the
 standalone PointPillar detector on single-agent samples (``LateFusionTrainDataset``: one random agent per frame, in its own frame,
-``late_fusion_dataset.py:33-49``) with ``FusedPointPillarLoss``; stage 2 (the default ``--stage hetero``) loads that checkpoint into
-``model.lidar_encoder`` (``--lidar_backbone_dir``, ``train_camera.py:109-114``) and freezes it.
+``late_fusion_dataset.py:33-49``) with ``FusedPointPillarLoss``; ``--stage camera_backbone`` (``opcl/fax_late_fusion.yaml``) does the
+same for the FAX camera detector on single camera-agent samples; stage 2 (the default ``--stage hetero``) loads those checkpoints
+into ``model.lidar_encoder`` (``--lidar_backbone_dir``, ``train_camera.py:109-114``) and, with ``--camera_encoder fax``, into
+``model.camera_encoder`` (``--camera_backbone_dir``) and freezes them.
 
     python -m hmvit_amd.trainer --epochs 2 --frames 8                      (one GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m hmvit_amd.trainer --epochs 2
     python -m hmvit_amd.trainer --stage lidar_backbone --model_dir runs/stage1          (stage 1)
     python -m hmvit_amd.trainer --lidar_backbone_dir runs/stage1 --model_dir runs/stage2 (stage 2)
+    python -m hmvit_amd.trainer --stage camera_backbone --grid 256 256 --model_dir runs/stage1_camera   (camera stage 1)
 """
 from __future__ import annotations
 
@@ -163,34 +166,15 @@ class SyntheticTrainDataset(R.SyntheticReplayDataset):
 
     def __init__(self, cfg, n_frames, post, n_agents=None, n_obj=12, seed=7, max_num=100, camera_ratio: float = 0.0,
                  ego_mode: str = "mixed", camera_image: int = 64):
-        """``camera_ratio`` / ``ego_mode``: the modality roll of ``basedataset.py:193-200`` - every non-ego agent is a camera agent
-        with probability ``camera_to_lidar_ratio``, the ego is ``lidar`` / ``camera`` or rolled like the others (``mixed``).  A frame
-        with camera agents carries ``camera`` / ``intrinsic`` / ``extrinsic`` / ``cav2cam_extrinsic`` for ALL its agents next to
-        the point clouds, as ``collate_batch`` hands them over (``mixed/intermediate_fusion_dataset.py:398-415``); ``mode`` says
-        which sensor of an agent the model reads."""
-        super().__init__(cfg, n_frames, n_agents=n_agents, n_obj=n_obj, seed=seed)
+        """``camera_ratio`` / ``ego_mode`` / ``camera_image``: the modality roll and camera tensors of the replay frames
+        (``SyntheticReplayDataset``)."""
+        super().__init__(cfg, n_frames, n_agents=n_agents, n_obj=n_obj, seed=seed, camera_ratio=camera_ratio, ego_mode=ego_mode,
+                         camera_image=camera_image)
         self.post, self.max_num = post, max_num
         self.anchors = post.generate_anchor_box()
-        self.camera_ratio, self.ego_mode, self.camera_image = camera_ratio, ego_mode, camera_image
-
-    def roll_modes(self, idx):
-        rs = np.random.RandomState(self.seed + 77 + 1000 * idx)
-        m = [0 if rs.uniform() < self.camera_ratio else 1 for _ in range(self.n_agents)]
-        if self.ego_mode == "lidar":
-            m[0] = 1
-        elif self.ego_mode == "camera":
-            m[0] = 0
-        return m
 
     def __getitem__(self, idx):
         frame = super().__getitem__(idx)
-        if self.camera_ratio > 0 or self.ego_mode == "camera":
-            from . import synthetic as S
-            modes = self.roll_modes(idx)
-            mode = torch.zeros(1, self.cfg["max_cav"], dtype=torch.float64)       # padding slots: 0 (base_camera_lidar_dataset.py:178)
-            mode[0, : self.n_agents] = torch.tensor(modes, dtype=torch.float64)
-            frame["mode"] = mode
-            frame.update(S.synthetic_cameras(self.n_agents, self.camera_image, seed=self.seed + 31 + 1000 * idx))
         boxes = frame["object_bbx_center_valid"]
         center = np.zeros((self.max_num, 7), np.float32)
         mask = np.zeros(self.max_num, np.float32)
@@ -216,11 +200,20 @@ class LateFusionTrainDataset(R.SyntheticReplayDataset):
     """The training side of ``CamLiLateFusionDataset`` (``mixed/late_fusion_dataset.py:33-49``) on the synthetic frames: sample
     ``i`` is ONE agent of frame ``i``, drawn with a seeded generator, in that agent's own frame - its point cloud as it sees it, the
     boxes moved into its frame (``cav_frame_boxes``) and kept when their centre lies inside its range (the reference's
-    ``mask_boxes_outside_range_numpy``), padded to ``max_num``, and the ``generate_label`` targets of its anchors."""
+    ``mask_boxes_outside_range_numpy``), padded to ``max_num``, and the ``generate_label`` targets of its anchors.
 
-    def __init__(self, cfg, n_samples, post, n_agents=None, n_obj=12, seed=7, max_num=100):
-        super().__init__(cfg, n_samples, n_agents=n_agents, n_obj=n_obj, seed=seed)
-        self.post, self.max_num = post, max_num
+    ``modality="camera"``: the camera detector's samples (``fax_late_fusion.yaml``: camera_to_lidar_ratio 1, ego camera) - every
+    agent of the frame is a camera agent and the sample carries the picked agent's four images, intrinsics and camera -> agent
+    extrinsics (``camera`` (4, H, W, 3), ``intrinsic`` (4, 3, 3), ``extrinsic`` (4, 4, 4)) instead of its cloud."""
+
+    def __init__(self, cfg, n_samples, post, n_agents=None, n_obj=12, seed=7, max_num=100, modality: str = "lidar",
+                 camera_image: int = 64):
+        if modality not in ("lidar", "camera"):
+            raise ValueError(f"modality must be 'lidar' or 'camera', got {modality!r}")
+        cam = modality == "camera"
+        super().__init__(cfg, n_samples, n_agents=n_agents, n_obj=n_obj, seed=seed, camera_ratio=1.0 if cam else 0.0,
+                         ego_mode="camera" if cam else "mixed", camera_image=camera_image)
+        self.post, self.max_num, self.modality = post, max_num, modality
         self.anchors = post.generate_anchor_box()
 
     def pick_cav(self, idx) -> int:
@@ -238,7 +231,9 @@ class LateFusionTrainDataset(R.SyntheticReplayDataset):
         mask = np.zeros(self.max_num, np.float32)
         center[: len(keep)], mask[: len(keep)] = boxes[keep], 1
         label = self.post.generate_label(gt_box_center=center, anchors=self.anchors, mask=mask)
-        return {"cloud": frame["clouds"][cav], "cav": cav, "lidar_pose": pose, "object_ids": keep, "object_bbx_center": center,
+        sensor = ({k: frame[k][cav] for k in ("camera", "intrinsic", "extrinsic")} if self.modality == "camera"
+                  else {"cloud": frame["clouds"][cav]})
+        return {**sensor, "cav": cav, "lidar_pose": pose, "object_ids": keep, "object_bbx_center": center,
                 "object_bbx_mask": mask, "label_dict": label}
 
 
@@ -264,6 +259,16 @@ def to_late_batch(samples: list, pre, device) -> dict:
     label = VoxelPostprocessor.collate_batch([s["label_dict"] for s in samples])
     return {"processed_lidar": lidar, "n_agents": len(samples),
             "label_dict": {k: v.to(device=device, dtype=torch.float32) for k, v in label.items()}}
+
+
+def to_late_camera_batch(samples: list, pre, device) -> dict:
+    """A list of camera ``LateFusionTrainDataset`` samples -> the camera detector's batch: ``camera`` (B, 4, H, W, 3), ``intrinsic``
+    (B, 4, 3, 3), ``extrinsic`` (B, 4, 4, 4) on the device and the stacked ``label_dict`` (``pre`` is not used: no point clouds)."""
+    from .postprocess import VoxelPostprocessor
+    label = VoxelPostprocessor.collate_batch([s["label_dict"] for s in samples])
+    batch = {k: torch.stack([s[k] for s in samples]).to(device=device, dtype=torch.float32) for k in ("camera", "intrinsic", "extrinsic")}
+    batch["label_dict"] = {k: v.to(device=device, dtype=torch.float32) for k, v in label.items()}
+    return batch
 
 
 def to_batch(frame: dict, pre, device) -> dict:
@@ -375,22 +380,75 @@ def build_lidar_backbone(args):
     return cfg, model, pre, post, ds, val
 
 
+def camera_detector_config(args) -> dict:
+    """``FaxCameraEncoder`` config of ``--grid`` / ``--camera_image`` (``synthetic.fax_camera_config``: raises ``ValueError`` for a
+    grid the FAX windows cannot tile)."""
+    from . import synthetic as S
+    return S.fax_camera_config(args.grid[0], args.grid[1], args.camera_image)
+
+
+def check_args(args) -> None:
+    """The argument checks that need no GPU: run before any device work (``main``) and by ``build``."""
+    stage = getattr(args, "stage", "hetero")
+    fax = getattr(args, "camera_encoder", "cvt") == "fax"
+    if getattr(args, "camera_backbone_dir", None):
+        if stage != "hetero" or not fax:
+            raise ValueError("--camera_backbone_dir loads a --stage camera_backbone checkpoint into the FAX camera slot: it needs "
+                             "--stage hetero with --camera_encoder fax")
+        if not (args.camera_ratio > 0 or args.ego_mode == "camera"):
+            raise ValueError("--camera_backbone_dir: no camera agents, so no camera slot (pass --camera_ratio > 0 or --ego_mode camera)")
+    if stage == "camera_backbone" or (stage == "hetero" and fax):
+        camera_detector_config(args)
+
+
+def build_camera_backbone(args):
+    """Stage 1 of the camera half (``fax_late_fusion.yaml``): the standalone FAX camera detector and batches of single camera-agent
+    samples.  Returns (cfg, model, pre, post, ds, val) like ``build_lidar_backbone``; ``pre`` is None (no point clouds)."""
+    from . import FaxCameraEncoder, VoxelPostprocessor
+    cfg = R.lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents, small=getattr(args, "small", False))
+    ccfg = camera_detector_config(args)
+    torch.manual_seed(args.seed)
+    model = FaxCameraEncoder(ccfg)
+    post = VoxelPostprocessor(R.postprocess_params(cfg), train=True)
+    batch = getattr(args, "batch", None) or 3
+    kw = dict(n_agents=args.agents, modality="camera", camera_image=args.camera_image)
+    ds = Batched(LateFusionTrainDataset(cfg, args.frames, post, seed=args.seed + 7, **kw), batch)
+    val = (Batched(LateFusionTrainDataset(cfg, args.val_frames, post, seed=args.seed + 100007, **kw), batch)
+           if args.val_frames > 0 else None)
+    return cfg, model, None, post, ds, val
+
+
 def build(args):
     from . import BevformerPointPillarHetero, SpVoxelPreprocessor, VoxelPostprocessor
-    if getattr(args, "stage", "hetero") == "lidar_backbone":
+    check_args(args)
+    stage = getattr(args, "stage", "hetero")
+    if stage == "lidar_backbone":
         return build_lidar_backbone(args)
+    if stage == "camera_backbone":
+        return build_camera_backbone(args)
     cfg = R.lidar_model_config(args.grid[0], args.grid[1], max_cav=args.agents, small=args.small)
     torch.manual_seed(args.seed)
     camera_encoder = None
     mixed = args.camera_ratio > 0 or args.ego_mode == "camera"
     if mixed:
-        # camera agents: the CVT lift in the model's camera slot, producing the LiDAR branch's (256, ny / 4, nx / 4) BEV map; frozen
-        # (train_camera.py's --fix_camera_backbone) unless --train_camera_backbone puts it on the tape (hm-vit_amd/camera_train.py)
+        # camera agents: the CVT lift (default) or the FAX detector's trunk (--camera_encoder fax) in the model's camera slot,
+        # producing the LiDAR branch's (256, ny / 4, nx / 4) BEV map; frozen (train_camera.py's --fix_camera_backbone) unless
+        # --train_camera_backbone puts it on the tape (hm-vit_amd/camera_train.py, fax_train.py)
         from . import synthetic as S
-        from .camera import CvtCameraEncoder
-        camera_encoder = CvtCameraEncoder(S.camera_config(args.camera_image, 18, bev_h=args.grid[1] // 2, bev_w=args.grid[0] // 2),
-                                          precision="f32" if args.precision == "f32" else "f16")
+        prec = "f32" if args.precision == "f32" else "f16"
+        if getattr(args, "camera_encoder", "cvt") == "fax":
+            from .fax import FaxCameraEncoder
+            camera_encoder = FaxCameraEncoder(camera_detector_config(args), precision=prec)
+        else:
+            from .camera import CvtCameraEncoder
+            camera_encoder = CvtCameraEncoder(S.camera_config(args.camera_image, 18, bev_h=args.grid[1] // 2, bev_w=args.grid[0] // 2),
+                                              precision=prec)
     model = BevformerPointPillarHetero(cfg, camera_encoder=camera_encoder, precision=args.precision)
+    if getattr(args, "camera_backbone_dir", None):
+        # train_camera.py:109-111: the stage-1 camera detector's weights into the camera slot (same module, same keys)
+        epoch, _ = load_saved_model(args.camera_backbone_dir, model.camera_encoder)
+        if epoch == 0:
+            raise FileNotFoundError(f"no net_epoch*.pth in {args.camera_backbone_dir}")
     if mixed and not getattr(args, "train_camera_backbone", False):
         model.fix_camera_backbone()                     # train_camera.py --fix_camera_backbone (the default here: faster steps)
     if getattr(args, "lidar_backbone_dir", None):
@@ -413,7 +471,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--agents", type=int, default=5)
-    ap.add_argument("--grid", type=int, nargs=2, default=[256, 128], metavar=("NX", "NY"))
+    ap.add_argument("--grid", type=int, nargs=2, default=None, metavar=("NX", "NY"),
+                    help="pillar grid; default 256 x 128, or 256 x 256 with the FAX camera detector (it needs a square grid)")
     ap.add_argument("--small", action="store_true", help="PointPillar layer_nums [1, 2, 2]")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16"], help="precision of the frozen encoder's kernels")
     ap.add_argument("--val_frames", type=int, default=2, help="frames of the validation split (0: no validation pass)")
@@ -426,23 +485,35 @@ def main(argv=None):
     ap.add_argument("--train_lidar_backbone", action="store_true",
                     help="do NOT freeze the LiDAR encoder: PointPillar trains too (hm-vit_amd/encoder_train.py)")
     ap.add_argument("--model_dir", default=None, help="folder with net_epoch%%d.pth to resume from / save into")
-    ap.add_argument("--stage", default="hetero", choices=["hetero", "lidar_backbone"],
+    ap.add_argument("--stage", default="hetero", choices=["hetero", "lidar_backbone", "camera_backbone"],
                     help="lidar_backbone: stage 1, the standalone PointPillar detector on single-agent samples "
-                         "(point_pillar_late_fusion.yaml); hetero: the HM-ViT model (stage 2)")
-    ap.add_argument("--batch", type=int, default=8, help="samples per step of --stage lidar_backbone (the yaml's batch_size)")
+                         "(point_pillar_late_fusion.yaml); camera_backbone: stage 1, the standalone FAX camera detector on single "
+                         "camera-agent samples (fax_late_fusion.yaml); hetero: the HM-ViT model (stage 2)")
+    ap.add_argument("--batch", type=int, default=None,
+                    help="samples per step of the stage-1 detectors (the yamls' batch_size: 8 lidar_backbone, 3 camera_backbone)")
     ap.add_argument("--lidar_backbone_dir", default=None,
                     help="folder with a stage-1 net_epoch%%d.pth: loaded into model.lidar_encoder before it is frozen")
+    ap.add_argument("--camera_encoder", default="cvt", choices=["cvt", "fax"],
+                    help="what fills the camera slot of stage 2: the CVT lift, or the FAX camera detector's trunk")
+    ap.add_argument("--camera_backbone_dir", default=None,
+                    help="folder with a --stage camera_backbone net_epoch%%d.pth: loaded into model.camera_encoder (needs "
+                         "--camera_encoder fax) before it is frozen")
     ap.add_argument("--fused_loss", action="store_true",
                     help="the HIP loss kernel pair (FusedPointPillarLoss) instead of the elementwise torch loss in stage 2")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (nccl = RCCL)")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
+    if args.grid is None:
+        args.grid = [256, 256] if args.stage == "camera_backbone" or args.camera_encoder == "fax" else [256, 128]
+    if args.batch is None:
+        args.batch = 3 if args.stage == "camera_backbone" else 8
+    check_args(args)                                   # ValueError before any device work
     if not torch.cuda.is_available():
         raise SystemExit("hm-vit_amd has no CPU path: this needs an MI355X")
     info = init_distributed_mode(args.backend)
     hypes = default_hypes(args.epochs)
-    stage1 = args.stage == "lidar_backbone"
+    stage1 = args.stage in ("lidar_backbone", "camera_backbone")
     if stage1 or args.fused_loss:
         hypes["loss"]["fused"] = True
     cfg, model, pre, post, ds, val = build(args)
@@ -452,7 +523,7 @@ def main(argv=None):
     model = model.to(f"cuda:{info['gpu']}")
     res = train(model, ds, pre, hypes, saved_path=args.model_dir, init_epoch=init_epoch, dist_info=info,
                 log=print if args.verbose and info["rank"] == 0 else None, val_dataset=val,
-                batch_fn=to_late_batch if stage1 else to_batch)
+                batch_fn={"lidar_backbone": to_late_batch, "camera_backbone": to_late_camera_batch}.get(args.stage, to_batch))
     if info["rank"] == 0:
         res.update(agents=args.agents, grid=args.grid, frames=args.frames, stage=args.stage)
         if stage1:
